@@ -39,7 +39,9 @@ timed AFTER the headline with the same K steps and reported as `value_source_pla
 Rank 0 prints ONE JSON line, under 8 KB: the contract fields, `roofline`, `cpu_baseline`, and the numbers that
 matter as top-level scalars (`kernel_ms`, `finish_ms`, `step_frac`, `fused_step_frac`, `fused_nested_step_frac`,
 `projected_efficiency_g8`, `value_first_allocation`, `value_source_placed`, `value_pipelined`, ...).  `--detail FILE`
-writes the full record -- every block with its explanations -- beside it.  `roofline` is for the dominant kernel (algorithmic bytes
+writes the full record -- every block with its explanations -- beside it; `--dump-outputs DIR` writes the per-ORF
+arrays the last timed step computed (every ORF, or a fixed seeded sample of a larger set) as DIR/<name>.npy, so that two
+builds can be compared output for output on the same seeded inputs.  `roofline` is for the dominant kernel (algorithmic bytes
 B = 4*sum(L) + 8*(n+1) + 24*n per launch over its HIP-event duration, vs the 8 TB/s
 HBM peak); `cpu_baseline` is the literal scipy restatement of the reference's phasescore
 (oracle/phasescore_literal.py) on all host cores, on a bounded sample of the same set.
@@ -100,6 +102,10 @@ def parse_args():
     ap.add_argument("--coverage-block", type=int, default=None, help="positions per block of the compact coverage (default: the export's, gather.COVERAGE_BLOCK)")
     ap.add_argument("--fused-steps", type=int, default=10)
     ap.add_argument("--seed", type=int, default=20260213)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (phase, valid, read_count, min_codon_cov, "
+                         "flags, status and the ORF index of each row) as DIR/<name>.npy in float64: every ORF, or a fixed seeded "
+                         "sample of 2^20 ORFs when there are more (N > 1: rank 0's slice)")
     ap.add_argument("--detail", default=None, help="write the FULL record (every block with its explanations: placement searches, per-slice "
                     "verification, gather-plan statistics, ...) to this file; stdout carries the compact line (< 8 KB) either way")
     return ap.parse_args()
@@ -120,6 +126,29 @@ def vbios_versions():
         if v and v not in seen:
             seen.append(v)
     return seen
+
+
+DUMP_MAX_ORFS = 1 << 20  # 7 float64 arrays of this length: 56 MiB, under the 64 MB a dump may take
+DUMP_SAMPLE_SEED = 12345
+
+
+def dump_outputs(out, n_orfs: int, path: str) -> None:
+    """--dump-outputs: the per-ORF arrays the caller of the timed path receives, as float64 .npy files (exact for every
+    integer column).  More ORFs than DUMP_MAX_ORFS: the same seeded sample of ORF indices in every run, sorted."""
+    import numpy as np
+    import torch
+
+    if n_orfs <= DUMP_MAX_ORFS:
+        rows = np.arange(n_orfs, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_orfs, size=DUMP_MAX_ORFS, replace=False)).astype(np.int64)
+    idx = torch.from_numpy(rows).to(out.phase.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "orf_index.npy"), rows.astype(np.float64))
+    for name in ("phase", "valid", "read_count", "min_codon_cov", "flags", "status"):
+        t = getattr(out, name)
+        if t is not None:
+            np.save(os.path.join(path, f"{name}.npy"), t.index_select(0, idx).cpu().numpy().astype(np.float64))
 
 
 def usable_cores():
@@ -821,6 +850,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if rccl is not None else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=rccl)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, n_orfs, args.dump_outputs)  # (before anything after the timed region reuses the output buffers)
 
     # per-kernel HIP-event timing (events recorded inside the library, on the same stream)
     timings: list = []

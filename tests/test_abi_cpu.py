@@ -167,3 +167,36 @@ def test_bench_line_of_the_full_size_record_fits_the_drivers_tail():
     for key in ("bound", "achieved", "peak", "unit", "frac", "traffic", "fetch_factor"):
         assert key in d["roofline"], key
     assert d["value"] == full["value"] and d["roofline"]["frac"] == full["roofline"]["frac"] and "workload" in d["config"]
+
+
+def test_bench_dump_outputs_samples_a_large_set_the_same_way_every_time(tmp_path, monkeypatch):
+    """bench.dump_outputs on host tensors: more ORFs than DUMP_MAX_ORFS -> the same sorted, seeded sample of rows in
+    every call, each column as float64 at those rows; at most DUMP_MAX_ORFS rows of every array."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+
+    from ribotricer_amd.engine import PhaseScores
+
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_MAX_ORFS", 1000)
+    n = 50_000
+    g = torch.Generator().manual_seed(3)
+    out = PhaseScores(torch.rand(n, dtype=torch.float64, generator=g), torch.randint(0, 99, (n,), dtype=torch.int32, generator=g),
+                      torch.randint(0, 1 << 40, (n,), dtype=torch.int64, generator=g), torch.randint(0, 99, (n,), dtype=torch.int32, generator=g),
+                      torch.randint(0, 8, (n,), dtype=torch.uint8, generator=g), torch.randint(0, 2, (n,), dtype=torch.uint8, generator=g))
+    dumps = []
+    for k in range(2):
+        bench.dump_outputs(out, n, str(tmp_path / str(k)))
+        dumps.append({f[:-4]: np.load(str(tmp_path / str(k) / f)) for f in os.listdir(str(tmp_path / str(k)))})
+    a, b = dumps
+    assert set(a) == {"orf_index", "phase", "valid", "read_count", "min_codon_cov", "flags", "status"}
+    rows = a["orf_index"].astype(np.int64)
+    assert rows.size == 1000 and (np.diff(rows) > 0).all() and rows[0] >= 0 and rows[-1] < n
+    for key in a:
+        assert a[key].dtype == np.float64 and a[key].shape == (1000,) and np.array_equal(a[key], b[key]), key
+        if key != "orf_index":
+            assert np.array_equal(a[key], getattr(out, key).numpy()[rows].astype(np.float64)), key
