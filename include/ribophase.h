@@ -659,6 +659,68 @@ int rp_phase_score_csr_dev_timed(int device, const int32_t *d_counts, const int6
                                  size_t workspace_bytes, int algo, const rp_plan *plan,
                                  void *hip_stream, float ms[4]);
 
+/*
+ * learn-cutoff (the reference's learn_cutoff.py: determine_cutoff_tsv).
+ *
+ * rp_cutoff_read_host reads ORF_type, transcript_type and phase_score of one `*_translating_ORFs.tsv` text the way
+ * pandas.read_csv(sep="\t", usecols=["ORF_ID", "ORF_type", "phase_score", "transcript_type"]) does (learn_cutoff.py:
+ * 60-76): per row the category codes of the two text columns (first-seen order; rp_cutoff_view.orf_cats /
+ * tx_cats hold the distinct raw strings, concatenated, with offsets) and the phase as float64 with pandas' default
+ * float converter (NA tokens -> NaN).  n_threads <= 0: one thread.  *status is RP_CUTOFF_OK, RP_CUTOFF_MISSING
+ * (a wanted column is absent: *missing has bit i for ORF_ID, ORF_type, phase_score, transcript_type) or one of the
+ * RP_CUTOFF_FALLBACK_* codes: a construct the reader does not model, at *bad_line; the caller reads that file with
+ * pandas.  *out is set only for RP_CUTOFF_OK.  Free with rp_cutoff_free.
+ */
+#define RP_CUTOFF_OK 0
+#define RP_CUTOFF_MISSING 1
+#define RP_CUTOFF_FALLBACK_QUOTE 2  /* a '"' byte */
+#define RP_CUTOFF_FALLBACK_CR 3     /* a '\r' not followed by '\n' */
+#define RP_CUTOFF_FALLBACK_FIELDS 4 /* a row whose field count differs from the header's */
+#define RP_CUTOFF_FALLBACK_PHASE 5  /* a phase text outside [+-]digits[.digits][(e|E)[+-]digits] and the NA tokens */
+#define RP_CUTOFF_FALLBACK_HEADER 6 /* a UTF-8 BOM, or a wanted column named twice */
+typedef struct rp_cutoff_cols rp_cutoff_cols;
+typedef struct rp_cutoff_view {
+    int64_t n_rows;
+    const int32_t *orf_type;
+    const int32_t *tx_type;
+    const double *phase;
+    int64_t n_orf_cats, n_tx_cats;
+    const char *orf_cats;
+    const int64_t *orf_cat_off;
+    const char *tx_cats;
+    const int64_t *tx_cat_off;
+} rp_cutoff_view;
+int rp_cutoff_read_host(const char *text, size_t len, int n_threads, int *status, int *missing, int64_t *bad_line,
+                        rp_cutoff_cols **out);
+int rp_cutoff_view_host(const rp_cutoff_cols *cols, rp_cutoff_view *view);
+void rp_cutoff_free(rp_cutoff_cols *cols);
+
+/*
+ * numpy's legacy MT19937 state after init_genrand(seed) and `offset` raw 32-bit words (what
+ * np.random.seed(seed) followed by drawing `offset` words leaves): key[624] and the return value pos (624 for offset 0).
+ * Host jump-ahead (characteristic polynomial by Berlekamp-Massey, x^offset mod p, correlation); the first call of the
+ * process builds the polynomial tables.  Negative on a NULL key.
+ */
+int rp_mt19937_state_host(uint32_t seed, uint64_t offset, uint32_t *key);
+
+/*
+ * The bootstrap of determine_cutoff_tsv (learn_cutoff.py:94-103) on `device`:
+ *   np.random.seed(seed); ribo_idx = choice(range(n_ribo), (k_ribo, reps)); rna_idx = choice(range(n_rna), (k_rna, reps))
+ *   ribo_medians = np.median(ribo_values[ribo_idx], axis=0); rna_medians likewise
+ * bit for bit: the masked-rejection draws of the legacy MT19937 stream (the RNA draws continue the stream; a group with
+ * n == 1 consumes no words), np.median's middle element / mean of the two middle elements / NaN rule.  Host arrays in
+ * and out; a group with k == 0 or reps == 0 leaves its medians untouched (np.median of an empty column is the caller's).
+ * end_key[624] / *end_pos: numpy's state after the last consumed word.  ms (may be NULL) receives 8 timings/sizes:
+ * [0] polynomial tables built by this call (host ms, 0 when cached), [1] jump tree, [2] count pass, [3] emit pass,
+ * [4] select, [5] whole call (ms), [6] chunks, [7] words per chunk.
+ * Synchronous.  Unlike the scoring entry points it allocates its own device memory (the words it needs are known only
+ * after the count pass); RP_ERR_WORKSPACE, with the bytes needed in the message, when the rank matrices do not fit.
+ * RP_ERR_SIZE for a negative size, a group with n == 0 that must draw, or k >= 2^31.
+ */
+int rp_bootstrap_medians_dev(int device, const double *ribo_values, int64_t n_ribo, int64_t k_ribo, const double *rna_values,
+                             int64_t n_rna, int64_t k_rna, int64_t reps, uint32_t seed, double *ribo_medians,
+                             double *rna_medians, uint32_t *end_key, int32_t *end_pos, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,23 @@ def make_filter(
     return fp
 
 
+class CutoffView(ctypes.Structure):
+    """rp_cutoff_view -- the columns learn-cutoff reads from one ``*_translating_ORFs.tsv``."""
+
+    _fields_ = [
+        ("n_rows", ctypes.c_int64),
+        ("orf_type", ctypes.c_void_p),
+        ("tx_type", ctypes.c_void_p),
+        ("phase", ctypes.c_void_p),
+        ("n_orf_cats", ctypes.c_int64),
+        ("n_tx_cats", ctypes.c_int64),
+        ("orf_cats", ctypes.c_void_p),
+        ("orf_cat_off", ctypes.c_void_p),
+        ("tx_cats", ctypes.c_void_p),
+        ("tx_cat_off", ctypes.c_void_p),
+    ]
+
+
 # every symbol include/ribophase.h declares: name -> (restype, argtypes)
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -154,6 +171,14 @@ SYMBOLS = {
     "rp_wig_pack_host": (_int, [_vp, _vp, _vp, _vp, _i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, ctypes.POINTER(_i64)]),
     "rp_wig_render_host": (ctypes.c_size_t, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "rp_measurement_tag": (ctypes.c_int, [ctypes.c_int]),
+    # learn-cutoff: the column reader (host), the MT19937 jump (host) and the bootstrap (device)
+    "rp_cutoff_read_host": (_int, [_vp, ctypes.c_size_t, _int, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_i64),
+                                   ctypes.POINTER(_vp)]),
+    "rp_cutoff_view_host": (_int, [_vp, ctypes.POINTER(CutoffView)]),
+    "rp_cutoff_free": (None, [_vp]),
+    "rp_mt19937_state_host": (_int, [ctypes.c_uint32, ctypes.c_uint64, _vp]),
+    "rp_bootstrap_medians_dev": (_int, [_int, _vp, _i64, _i64, _vp, _i64, _i64, _i64, ctypes.c_uint32, _vp, _vp, _vp,
+                                        ctypes.POINTER(ctypes.c_int32), _vp]),
 }
 
 _lib = None

@@ -6,6 +6,9 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <chrono>
+#include <memory>
+#include <string>
 
 #include <cstdarg>
 #include <cstdio>
@@ -1605,3 +1608,88 @@ extern "C" int rp_debug_replay_stamps(unsigned long long *out8, int reset)
 }
 #endif
 
+
+// ---- learn-cutoff: the column reader, the host MT19937 jump and the bootstrap ---------------------------------------
+#include "rp_cutoff_reader.hpp"
+#include "rp_mt19937.hpp"
+#include "rp_bootstrap.hpp"
+
+struct rp_cutoff_cols {
+    rpcut::Columns c;
+    std::string orf_cats, tx_cats;
+    std::vector<int64_t> orf_off, tx_off;
+};
+
+
+extern "C" {
+
+int rp_cutoff_read_host(const char *text, size_t len, int n_threads, int *status, int *missing, int64_t *bad_line,
+                        rp_cutoff_cols **out)
+{
+    if (!out || !status) return fail(RP_ERR_NULL, "out / status is null");
+    *out = nullptr;
+    if (!text && len > 0) return fail(RP_ERR_NULL, "text is null but len > 0");
+    rp_cutoff_cols *h = new (std::nothrow) rp_cutoff_cols;
+    if (!h) return fail(RP_ERR_SIZE, "out of memory");
+    try {
+        *status = rpcut::read(text ? text : "", len, n_threads, h->c);
+        if (missing) *missing = h->c.missing;
+        if (bad_line) *bad_line = h->c.bad_line;
+        if (*status != rpcut::kOk) {
+            delete h;
+            return RP_OK;
+        }
+        auto pack = [](const std::vector<std::string> &cats, std::string &blob, std::vector<int64_t> &off) {
+            off.assign(1, 0);
+            for (const auto &s : cats) {
+                blob += s;
+                off.push_back((int64_t)blob.size());
+            }
+        };
+        pack(h->c.orf_cats, h->orf_cats, h->orf_off);
+        pack(h->c.tx_cats, h->tx_cats, h->tx_off);
+    } catch (const std::bad_alloc &) {
+        delete h;
+        return fail(RP_ERR_SIZE, "out of memory while reading the columns");
+    }
+    *out = h;
+    return RP_OK;
+}
+
+int rp_cutoff_view_host(const rp_cutoff_cols *cols, rp_cutoff_view *view)
+{
+    if (!cols || !view) return fail(RP_ERR_NULL, "cols / view is null");
+    view->n_rows = (int64_t)cols->c.phase.size();
+    view->orf_type = cols->c.orf_type.data();
+    view->tx_type = cols->c.tx_type.data();
+    view->phase = cols->c.phase.data();
+    view->n_orf_cats = (int64_t)cols->c.orf_cats.size();
+    view->n_tx_cats = (int64_t)cols->c.tx_cats.size();
+    view->orf_cats = cols->orf_cats.data();
+    view->orf_cat_off = cols->orf_off.data();
+    view->tx_cats = cols->tx_cats.data();
+    view->tx_cat_off = cols->tx_off.data();
+    return RP_OK;
+}
+
+void rp_cutoff_free(rp_cutoff_cols *cols) { delete cols; }
+
+int rp_mt19937_state_host(uint32_t seed, uint64_t offset, uint32_t *key)
+{
+    if (!key) return fail(RP_ERR_NULL, "key is null");
+    return rpmt::state_after(seed, offset, key);
+}
+
+int rp_bootstrap_medians_dev(int device, const double *ribo_values, int64_t n_ribo, int64_t k_ribo, const double *rna_values,
+                             int64_t n_rna, int64_t k_rna, int64_t reps, uint32_t seed, double *ribo_medians,
+                             double *rna_medians, uint32_t *end_key, int32_t *end_pos, float *ms)
+{
+    std::unique_ptr<DeviceGuard> guard;
+    return rpboot::bootstrap_medians(ribo_values, n_ribo, k_ribo, rna_values, n_rna, k_rna, reps, seed, ribo_medians, rna_medians,
+                                     end_key, end_pos, ms, [&] {
+                                         guard.reset(new DeviceGuard(device));
+                                         return guard->rc;
+                                     }, fail);
+}
+
+}  // extern "C"
