@@ -7,9 +7,9 @@ P-site counts, resident in HBM):
     N = 1   configs[2]  the whole set on one MI355X
     N > 1   configs[3]  the SAME set cut into N nt-balanced ORF-index slices
                         (ribotricer_amd/sharding.py), one slice per GPU, no collective on
-                        the data path -> "scaling": "strong".  After the timed steps rank 0
-                        scores the whole set on its own GPU and checks that the
-                        concatenation of the ranks' results equals it.
+                        the data path -> "scaling": "strong".  With --full, after the timed
+                        steps rank 0 scores the whole set on its own GPU and checks that
+                        the concatenation of the ranks' results equals it.
 A "step" is one pass of the hot path over the rank's slice: libribophase
 rp_phase_score_csr_plan_dev = scoring kernel (rp::k_tile_score) + per-ORF finish kernel.
 The tile plan (tile index + offsets validation, rp_plan_create_dev) depends on the index
@@ -18,6 +18,7 @@ sample; its time is reported as `plan_build_ms`, and `value_single_sample` is th
 the plan rebuilt inside every step (an index used for ONE sample).
 
     python bench.py --gpus 1 --steps 50 --warmup 5
+    python bench.py --gpus 1 --steps 50 --warmup 5 --full   (the headline, then everything else below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N --steps K --warmup W      (no launcher: bench.py starts its own N ranks)
@@ -36,16 +37,20 @@ where the caller's allocation put them for the headline: no product path moves a
 as well would give (`engine.tune_source`: copies behind spacers until the kernel runs at the fast class's rate) is
 timed AFTER the headline with the same K steps and reported as `value_source_placed` (`--no-tune-source`: skip).
 
-Rank 0 prints ONE JSON line, under 8 KB: the contract fields, `roofline`, `cpu_baseline`, and the numbers that
-matter as top-level scalars (`kernel_ms`, `finish_ms`, `step_frac`, `fused_step_frac`, `fused_nested_step_frac`,
-`projected_efficiency_g8`, `value_first_allocation`, `value_source_placed`, `value_pipelined`, ...).  `--detail FILE`
-writes the full record -- every block with its explanations -- beside it; `--dump-outputs DIR` writes the per-ORF
+A PLAIN run does what the headline needs and nothing more: it sets up (the set, the plan, the workspace search and
+the first-allocation steps before it), warms up, times the K steps, writes --dump-outputs and prints rank 0's ONE JSON
+line: the contract fields, `config`, `per_rank` and (search run) `value_first_allocation`.  `--dump-outputs DIR` writes the per-ORF
 arrays the last timed step computed (every ORF, or a fixed seeded sample of a larger set) as DIR/<name>.npy, so that two
-builds can be compared output for output on the same seeded inputs.  `roofline` is for the dominant kernel (algorithmic bytes
+builds can be compared output for output on the same seeded inputs; `--detail FILE` writes the full record -- every
+block with its explanations -- beside the line.  Everything else runs only with `--full`, after the timed steps.
+
+With --full the line (under 8 KB) also carries `roofline`, `cpu_baseline`, `verify` and the numbers that matter as
+top-level scalars (`kernel_ms`, `finish_ms`, `step_frac`, `fused_step_frac`, `fused_nested_step_frac`,
+`projected_efficiency_g8`, `value_source_placed`, `value_pipelined`, ...).  `roofline` is for the dominant kernel (algorithmic bytes
 B = 4*sum(L) + 8*(n+1) + 24*n per launch over its HIP-event duration, vs the 8 TB/s
 HBM peak); `cpu_baseline` is the literal scipy restatement of the reference's phasescore
 (oracle/phasescore_literal.py) on all host cores, on a bounded sample of the same set.
-AFTER the timed region (N = 1): `verify` -- head / middle / tail slices of 20 000 ORFs and the
+AFTER the timed region (N = 1, --full): `verify` -- head / middle / tail slices of 20 000 ORFs and the
 ORFs around 2^31 / 2^32 nt of what the steps computed, against the C oracle on the same bytes
 (integers bit-exact, phase <= 1e-6, exact frame ties bit for bit) -- and `fused` / `fused_nested` -- what
 the drop-in export runs by default (gather + score fused, rp::k_tile_score<true>, with RP_FILTER_PRINTED_ONLY as
@@ -88,20 +93,26 @@ def parse_args():
                     help="strong: one set sharded over the GPUs (configs[3]); weak: --orfs ORFs on every GPU")
     ap.add_argument("--algo", default="auto", choices=["auto", "wave", "tile"])
     ap.add_argument("--no-plan", action="store_true", help="rebuild the tile index inside every step")
-    ap.add_argument("--cpu-sample", type=int, default=12000, help="ORFs per process for the CPU baseline (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=12000, help="ORFs per process for the CPU baseline (--full; 0 = skip)")
     ap.add_argument("--cpu-cores", type=int, default=0, help="processes for the CPU baseline (default: the usable cores, at most 64)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the oracle check of head / middle / tail slices (N = 1) and the concat == whole check (N > 1)")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the oracle check of head / middle / tail slices (N = 1) and the concat == whole check (N > 1)")
     ap.add_argument("--no-tune-workspace", action="store_true", help="keep the record workspace where the first allocation put it (engine.tune_workspace off)")
-    ap.add_argument("--no-tune-source", action="store_true", help="keep the synthetic counts / coverage where the first allocation put them (engine.tune_source off)")
-    ap.add_argument("--no-pipelined", action="store_true", help="skip the two-stream many-samples section (N = 1)")
-    ap.add_argument("--no-slice-projection", action="store_true", help="skip timing rank 0's slice of the 2 / 4 / 8-GPU runs on this one GPU (N = 1)")
-    ap.add_argument("--no-fused", action="store_true", help="skip the fused gather + score section (N = 1)")
-    ap.add_argument("--no-fused-nested", action="store_true", help="skip the nested-index fused section (N = 1)")
-    ap.add_argument("--no-fused-exons", action="store_true", help="skip the fused section on the run's own length law (N = 1; counter passes that want the nested launches alone)")
+    ap.add_argument("--no-tune-source", action="store_true", help="with --full: keep the synthetic counts / coverage where the first allocation put them (engine.tune_source off)")
+    ap.add_argument("--no-pipelined", action="store_true", help="with --full: skip the two-stream many-samples section (N = 1); "
+                    "with or without --full, the headline's record workspace is then one workspace instead of a block of two")
+    ap.add_argument("--no-slice-projection", action="store_true", help="with --full: skip timing rank 0's slice of the 2 / 4 / 8-GPU runs on this one GPU (N = 1)")
+    ap.add_argument("--no-fused", action="store_true", help="with --full: skip the fused gather + score section (N = 1)")
+    ap.add_argument("--no-fused-nested", action="store_true", help="with --full: skip the nested-index fused section (N = 1)")
+    ap.add_argument("--no-fused-exons", action="store_true", help="with --full: skip the fused section on the run's own length law (N = 1; counter passes that want the nested launches alone)")
     ap.add_argument("--dense-coverage", action="store_true", help="fused sections over the dense coverage layout (default: the compact one the export builds)")
     ap.add_argument("--coverage-block", type=int, default=None, help="positions per block of the compact coverage (default: the export's, gather.COVERAGE_BLOCK)")
     ap.add_argument("--fused-steps", type=int, default=10)
     ap.add_argument("--seed", type=int, default=20260213)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the bench measures and checks: per-kernel times and the roofline, the "
+                         "slice projection, the single-sample, two-stream and source-placed rates, the oracle checks (N = 1) and the "
+                         "concat == whole check (N > 1), the fused sections, the plain-read yardstick and the CPU baselines.  Without "
+                         "it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (phase, valid, read_count, min_codon_cov, "
                          "flags, status and the ORF index of each row) as DIR/<name>.npy in float64: every ORF, or a fixed seeded "
@@ -568,8 +579,8 @@ def _pick(d, keys):
 
 
 def compact_line(full: dict) -> dict:
-    """The ONE JSON line: the contract fields, the roofline and cpu_baseline blocks, and every number a reader of the
-    driver's record needs as a top-level scalar -- under 8 KB (tests/test_gpu_bench_contract.py).  The explanations
+    """The ONE JSON line: the contract fields and the config, and (--full) the roofline and cpu_baseline blocks and every
+    number a reader of the driver's record needs as a top-level scalar -- under 8 KB (tests/test_gpu_bench_contract.py).  The explanations
     (`what` texts), the placement searches' step lists, per-slice verification records, gather-plan statistics and
     per-process baselines live in the full record (`--detail FILE`; DESIGN.md section 6 explains every field)."""
     line = _pick(full, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -585,21 +596,22 @@ def compact_line(full: dict) -> dict:
                                                  "settled": wp.get("settled")}
     else:
         line["config"]["workspace_placement"] = {"searched": False}
-    roof = full["roofline"]
-    line["roofline"] = _pick(roof, ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source", "fetch_factor", "kernel", "rank",
-                                    "node_achieved", "node_peak", "kernel_ms", "algorithmic_bytes_per_launch", "step_device_ms", "step_achieved",
-                                    "step_frac", "frac_of_stream_read"))
-    line["roofline"]["finish_ms"] = roof["aux_kernels_ms"]["orf_finish"]
-    line["roofline"]["tile_index_ms"] = roof["aux_kernels_ms"]["tile_index"]
-    if roof.get("stream_read"):
-        line["roofline"]["stream_read_GBps"] = roof["stream_read"]["GBps"]
-        pen = roof["stream_read"].get("record_write_penalty")
-        if pen:
-            line["roofline"]["record_write_penalty"] = [round(x, 4) for x in pen["penalty"]]
-    # the scalars (they survive a flattening reader)
-    line["kernel_ms"] = roof["kernel_ms"]
-    line["finish_ms"] = roof["aux_kernels_ms"]["orf_finish"]
-    line["step_frac"] = roof["step_frac"]
+    roof = full.get("roofline")  # (--full only)
+    if roof is not None:
+        line["roofline"] = _pick(roof, ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source", "fetch_factor", "kernel", "rank",
+                                        "node_achieved", "node_peak", "kernel_ms", "algorithmic_bytes_per_launch", "step_device_ms", "step_achieved",
+                                        "step_frac", "frac_of_stream_read"))
+        line["roofline"]["finish_ms"] = roof["aux_kernels_ms"]["orf_finish"]
+        line["roofline"]["tile_index_ms"] = roof["aux_kernels_ms"]["tile_index"]
+        if roof.get("stream_read"):
+            line["roofline"]["stream_read_GBps"] = roof["stream_read"]["GBps"]
+            pen = roof["stream_read"].get("record_write_penalty")
+            if pen:
+                line["roofline"]["record_write_penalty"] = [round(x, 4) for x in pen["penalty"]]
+        # the scalars (they survive a flattening reader)
+        line["kernel_ms"] = roof["kernel_ms"]
+        line["finish_ms"] = roof["aux_kernels_ms"]["orf_finish"]
+        line["step_frac"] = roof["step_frac"]
     for key in ("value_first_allocation", "value_source_placed", "value_pipelined", "value_one_stream_repeat", "value_single_sample"):
         if key in full:
             line[key] = full[key]
@@ -639,7 +651,8 @@ def compact_line(full: dict) -> dict:
     if "single_sample" in full:
         line["single_sample_ms_per_step"] = full["single_sample"]["ms_per_step"]
     line["per_rank"] = [_pick(r, ("rank", "device", "orfs", "nt", "kernel_ms", "finish_ms", "step_device_ms", "frac")) for r in full["per_rank"]]
-    line["quality"] = full["quality"]
+    if "quality" in full:
+        line["quality"] = full["quality"]
     if "verify" in full:
         v = full["verify"]
         line["verify"] = _pick(v, ("ok", "orfs_checked", "max_abs_dphase", "ties_bit_exact", "read_count_checksum_ok", "read_count_checksum"))
@@ -666,9 +679,9 @@ def main():
     if os.environ.get("RP_BENCH_LAUNCH_ONLY") == "1":
         return launch_only(rank, world)
 
-    # CPU-baseline workers first: they must exist before this process initialises the GPU
+    # CPU-baseline workers first (--full): they must exist before this process initialises the GPU
     pool = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         from oracle.cpu_pool import CpuPool
 
         pool = CpuPool(args.cpu_cores if args.cpu_cores > 0 else min(usable_cores(), 64))
@@ -757,7 +770,9 @@ def main():
     total_nt = counts.numel()
     eng = PhaseScoreEngine(dev)
     if world == 1 and not args.no_pipelined:
-        eng.workspace_copies = 2  # (a stream's workspace is a block of two: the second serves the other stream of the two-stream trial)
+        # (a stream's workspace is a block of two: the second serves the other stream of the two-stream trial -- with or
+        # without --full, so that the headline's steps write into the same kind of block either way)
+        eng.workspace_copies = 2
     thresholds = make_filter()
     algo = args.algo
     resolved = ("tile" if total_nt >= (2 << 20) else "wave") if algo == "auto" else algo
@@ -781,7 +796,8 @@ def main():
         # placements, keeps the fastest and frees the rest -- exactly what the drop-in export does once per cached index
         # (detect_orfs.score_index).  Reported in config.workspace_placement; --no-tune-workspace switches it off.
         # Before it: the same step on the workspace as FIRST allocated (what a process gets without the search),
-        # reported as value_first_allocation.
+        # reported as value_first_allocation.  These steps run without --full too: they bring the clocks up before the
+        # search times its first candidate, so that the search keeps the same workspace with and without --full.
         lib_tag = _lib.load()
         was_tag = lib_tag.rp_measurement_tag(1)  # (these launches and the search's run under the second kernel name: a profiler's
         n_first = max(3, min(args.steps, 20))    #  statistics of rp::k_tile_score hold the headline's launches only)
@@ -853,13 +869,16 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(out, n_orfs, args.dump_outputs)  # (before anything after the timed region reuses the output buffers)
 
+    # ---- --full: everything below that is not the headline -------------------------------------
     # per-kernel HIP-event timing (events recorded inside the library, on the same stream)
-    timings: list = []
-    for _ in range(max(5, min(args.steps, 20))):
-        eng.score(counts, offsets, thresholds=thresholds, algo=algo, reuse_outputs=True, plan=plan, timings=timings)
-    k_index = sum(t[0] for t in timings) / len(timings)
-    k_main = sum(t[1] for t in timings) / len(timings)
-    k_fin = sum(t[2] for t in timings) / len(timings)
+    k_index = k_main = k_fin = None
+    if args.full:
+        timings: list = []
+        for _ in range(max(5, min(args.steps, 20))):
+            eng.score(counts, offsets, thresholds=thresholds, algo=algo, reuse_outputs=True, plan=plan, timings=timings)
+        k_index = sum(t[0] for t in timings) / len(timings)
+        k_main = sum(t[1] for t in timings) / len(timings)
+        k_fin = sum(t[2] for t in timings) / len(timings)
     # The 1 -> 8 GPU curve (BASELINE configs[3]) PROJECTED from the one GPU at hand: for G in {2, 4, 8}, rank 0's
     # nt-balanced slice of the SAME set (sharding.slice_bounds -- exactly what `--gpus G` gives rank 0: views of the
     # resident counts / offsets, a tile plan of its own) timed with the headline protocol.  There is no collective and
@@ -868,7 +887,7 @@ def main():
     # the projection cannot see is anything the ranks share on a real node (host launch threads, power); the driver's
     # --gpus N runs measure that.
     projection = None
-    if world == 1 and strong and plan is not None and not args.no_slice_projection and n_orfs >= 64:
+    if args.full and world == 1 and strong and plan is not None and not args.no_slice_projection and n_orfs >= 64:
         from ribotricer_amd.engine import TilePlan
 
         step1_ms = 1e3 * elapsed / max(1, args.steps)
@@ -921,7 +940,7 @@ def main():
     # Timed separately (same K-step protocol, fewer steps): the tile index, descriptors and head
     # rows rebuilt inside every step (rp_phase_score_csr_dev without a plan).
     single_ms = None
-    if plan is not None:
+    if args.full and plan is not None:
         n_single = max(3, min(args.steps, 10))
         for _ in range(2):
             eng.score(counts, offsets, thresholds=thresholds, algo="tile", reuse_outputs=True, plan=None)
@@ -944,7 +963,7 @@ def main():
     # (engine.tune_workspace(copies=2) / share_placed_workspace), not from searches of their own.  Same work per step as the
     # headline (every sample is scored and finished); reported BESIDE `value`, never instead of it.
     pipelined = None
-    if world == 1 and plan is not None and not args.no_pipelined and total_nt >= (64 << 20):
+    if args.full and world == 1 and plan is not None and not args.no_pipelined and total_nt >= (64 << 20):
         lanes = [torch.cuda.Stream(device=dev) for _ in range(2)]
         tag_lib = _lib.load()
         tag_was = tag_lib.rp_measurement_tag(1)  # (overlapped launches last longer: kept out of a profiler's rp::k_tile_score statistics)
@@ -999,7 +1018,7 @@ def main():
     # and the same K steps are timed again: value_source_placed.  No product path moves a caller's array -- which is why
     # this is not `value` -- but a caller who owns his allocation can.
     source_placed = None
-    if placement is not None and not args.no_tune_source and world == 1:
+    if args.full and placement is not None and not args.no_tune_source and world == 1:
         tag_lib = _lib.load()
         tag_was = tag_lib.rp_measurement_tag(1)  # (kept out of a profiler's rp::k_tile_score statistics)
         counts_first = counts
@@ -1020,10 +1039,11 @@ def main():
         del counts_first
         tag_lib.rp_measurement_tag(tag_was)
     rank_bytes = 4 * total_nt + 8 * (n_orfs + 1) + 24 * n_orfs  # SURVEY 8(d), this rank's slice
-    per_rank = {"rank": rank, "device": local_dev, "orfs": n_orfs, "nt": total_nt, "kernel_ms": k_main, "finish_ms": k_fin,
-                "step_device_ms": dev_ms_per_step, "algorithmic_bytes_per_launch": rank_bytes,
-                "achieved": rank_bytes / (k_main * 1e-3) / 1e9 if k_main > 0 else 0.0,
-                "frac": rank_bytes / (k_main * 1e-3) / 1e9 / HBM_PEAK_GBS if k_main > 0 else 0.0}
+    per_rank = {"rank": rank, "device": local_dev, "orfs": n_orfs, "nt": total_nt, "step_device_ms": dev_ms_per_step,
+                "algorithmic_bytes_per_launch": rank_bytes}
+    if k_main is not None:
+        per_rank.update(kernel_ms=k_main, finish_ms=k_fin, achieved=rank_bytes / (k_main * 1e-3) / 1e9 if k_main > 0 else 0.0,
+                        frac=rank_bytes / (k_main * 1e-3) / 1e9 / HBM_PEAK_GBS if k_main > 0 else 0.0)
     ranks = [per_rank]
     if dist is not None:
         ranks = [None] * world
@@ -1031,7 +1051,7 @@ def main():
 
     # ---- N > 1: the concatenation of the ranks' results must equal the one-GPU result ----------
     verify = None
-    if dist is not None and strong and not args.no_verify:
+    if args.full and dist is not None and strong and not args.no_verify:
         keys = ("phase", "valid", "read_count", "min_codon_cov", "flags", "status")
         mine = {k: getattr(out, k) for k in keys}
         if rank == 0:
@@ -1069,7 +1089,7 @@ def main():
             sys.exit(2)
 
     quality = None
-    if rank == 0:  # (now: the fused sections below reuse the engine's output buffers)
+    if args.full and rank == 0:  # (now: the fused sections below reuse the engine's output buffers)
         hf = out.flags
         quality = {
             "tie_flag_rate": float((hf & _lib.FLAG_TIE).ne(0).double().mean()) if n_orfs else 0.0,
@@ -1081,7 +1101,7 @@ def main():
             "left_open": int((hf & _lib.FLAG_UNRESOLVED).ne(0).sum()) if n_orfs else 0,
         }
     fused = fused_nested = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_verify and n_orfs > 0:
             concat_check = verify  # (RP_BENCH_FORCE_DIST: the N-rank check ran with one rank)
             verify = verify_slices(out, counts, offsets, n_orfs)
@@ -1100,7 +1120,7 @@ def main():
             sys.exit(2)
 
     stream_read = None
-    if rank == 0 and world == 1 and total_nt >= (1 << 22):
+    if args.full and rank == 0 and world == 1 and total_nt >= (1 << 22):
         # After the timed region: what does a plain read of the SAME counts buffer reach in this process, on this
         # box, right now?  (csrc/stream_probe.hip: 32 KiB pieces DMA'd into LDS by one loader wave, four workgroups
         # per CU -- the scoring kernel's skeleton and nothing else.)  The scoring kernel was seen between 2.6 and
@@ -1129,14 +1149,6 @@ def main():
             stream_read = None
 
     if rank == 0:
-        # N > 1: the roofline block is the SLOWEST rank's kernel (the one the max-over-ranks time follows), per launch
-        # and per GPU like at N = 1; `node_achieved` = all ranks' bytes over that slowest kernel's time
-        slow = max(ranks, key=lambda r: r["kernel_ms"])
-        algo_bytes = slow["algorithmic_bytes_per_launch"]
-        k_main, k_fin, dev_ms_per_step = slow["kernel_ms"], slow["finish_ms"], slow["step_device_ms"]
-        achieved = algo_bytes / (k_main * 1e-3) / 1e9
-        node_bytes = sum(r["algorithmic_bytes_per_launch"] for r in ranks)
-        traffic, traffic_src, fetch_factor = (measured_traffic(args.cfg, n_orfs, resolved, args.seed) if world == 1 else (None, None, None))
         nt_set = int(offsets_set[-1]) if strong else total_nt * world
         result = {
             "metric": "ORFs phase-scored/sec (whole node)",
@@ -1174,7 +1186,18 @@ def main():
                             ("external (torch.distributed.run)" if world > 1 else "none"),
                 "control_backend": backend,
             },
-            "roofline": {
+            "per_rank": ranks,
+        }
+        if args.full:
+            # N > 1: the roofline block is the SLOWEST rank's kernel (the one the max-over-ranks time follows), per launch
+            # and per GPU like at N = 1; `node_achieved` = all ranks' bytes over that slowest kernel's time
+            slow = max(ranks, key=lambda r: r["kernel_ms"])
+            algo_bytes = slow["algorithmic_bytes_per_launch"]
+            k_main, k_fin, dev_ms_per_step = slow["kernel_ms"], slow["finish_ms"], slow["step_device_ms"]
+            achieved = algo_bytes / (k_main * 1e-3) / 1e9
+            node_bytes = sum(r["algorithmic_bytes_per_launch"] for r in ranks)
+            traffic, traffic_src, fetch_factor = (measured_traffic(args.cfg, n_orfs, resolved, args.seed) if world == 1 else (None, None, None))
+            result["roofline"] = {
                 "bound": "hbm",
                 "achieved": achieved,
                 "peak": HBM_PEAK_GBS,
@@ -1195,10 +1218,8 @@ def main():
                 "step_frac": algo_bytes / (dev_ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
                 "stream_read": stream_read,
                 "frac_of_stream_read": (achieved / stream_read["GBps"]) if stream_read else None,
-            },
-            "per_rank": ranks,
-            "quality": quality,
-        }
+            }
+            result["quality"] = quality
         if first_alloc_ms is not None:
             result["value_first_allocation"] = (n_job / (first_alloc_ms * 1e-3)) if world == 1 else None
             result["first_allocation"] = {"ms_per_step": first_alloc_ms, "steps": max(3, min(args.steps, 20)),

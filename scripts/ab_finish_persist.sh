@@ -4,7 +4,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 for r in $(seq 1 ${1:-2}); do
 for P in 0 1 2 4; do
-  RP_FINISH_PERSIST=$P timeout 600 python3 bench.py --steps 30 --warmup 5 --cpu-sample 0 --no-pipelined --no-fused-nested --no-verify 2>/dev/null | python3 -c "
+  RP_FINISH_PERSIST=$P timeout 600 python3 bench.py --full --steps 30 --warmup 5 --cpu-sample 0 --no-pipelined --no-fused-nested --no-verify 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; f=d['fused']; s=d['slice_projection']['slices']
 print('persist=$P cfg3 kernel %.4f finish %.4f step %.4f | fused kernel %.4f finish %.4f | slice8 step %.4f finish %.4f eff %.3f | slice2 finish %.4f' % (

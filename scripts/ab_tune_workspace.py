@@ -8,7 +8,7 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for k in range(2 * (int(sys.argv[1]) if len(sys.argv) > 1 else 3)):
     extra = ["--no-tune-workspace"] if k % 2 == 0 else []
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "30", "--warmup", "5", "--cpu-sample", "0", "--no-fused"] + extra,
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "30", "--warmup", "5", "--cpu-sample", "0", "--no-fused"] + extra,
                          capture_output=True, text=True)
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     if not line:

@@ -4,7 +4,7 @@
 """Does the PRODUCT get the placement the bench enjoys?  (round-3 verdict, item 2)
 
 P fresh processes each of
-  bench     `python bench.py --steps 30 --warmup 5 --cpu-sample 0 --no-fused`: kernel time of the timed steps (after
+  bench     `python bench.py --full --steps 30 --warmup 5 --cpu-sample 0 --no-fused`: kernel time of the timed steps (after
             engine.tune_workspace), the step on the workspace as first allocated, memory reserved after the search;
   product   this file with `child`: `export_orf_coverages` (default mode) twice on a nested candidate index
             (scripts/gen_big_index.cpp) -- the first call parses, plans and places the workspace (once per cached
@@ -83,7 +83,7 @@ def main() -> None:
     procs = int(sys.argv[1]) if len(sys.argv) > 1 else 5
     n_orfs = int(sys.argv[2]) if len(sys.argv) > 2 else 6_000_000
     for k in range(procs):
-        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "30", "--warmup", "5", "--cpu-sample", "0", "--no-fused"],
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "30", "--warmup", "5", "--cpu-sample", "0", "--no-fused"],
                              capture_output=True, text=True)
         line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
         if not line:

@@ -1,4 +1,4 @@
-run() { echo "== $*"; timeout 600 python bench.py "$@" 2>/tmp/err.txt | python -c "
+run() { echo "== $*"; timeout 600 python bench.py --full "$@" 2>/tmp/err.txt | python -c "
 import json,sys
 t=sys.stdin.read().strip().splitlines()
 d=json.loads(t[-1]) if t else {}

@@ -6,7 +6,7 @@ cd ${GRAFT_REPO_ROOT:-.}
 mkdir -p $OUT
 for p in $(seq 1 $P); do
   bash scripts/box_kind.sh 2>/dev/null | tail -1
-  timeout 600 python3 bench.py --cpu-sample 0 --no-fused-nested "$@" > $OUT/bench_$p.json 2> $OUT/bench_$p.err
+  timeout 600 python3 bench.py --full --cpu-sample 0 --no-fused-nested "$@" > $OUT/bench_$p.json 2> $OUT/bench_$p.err
   python3 - $OUT/bench_$p.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -1,7 +1,7 @@
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp; rm -rf /tmp/kc
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kc -o s -- python3 $R/bench.py --steps 5 --warmup 2 --cpu-sample 0 --no-verify > /tmp/kc_bench.json 2>/dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kc -o s -- python3 $R/bench.py --full --steps 5 --warmup 2 --cpu-sample 0 --no-verify > /tmp/kc_bench.json 2>/dev/null
 python3 - <<'PY'
 import csv, glob, json
 for f in glob.glob("/tmp/kc/**/*kernel_stats.csv", recursive=True):

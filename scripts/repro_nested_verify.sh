@@ -8,7 +8,7 @@ mkdir -p $R/gpurun_out
 cd /tmp
 for i in $(seq 1 $N); do
   rm -rf /tmp/rp_$i; mkdir -p /tmp/rp_$i
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_$i -o s -- python3 $R/bench.py --steps 20 --warmup 3 --cpu-sample 0 > /tmp/rp_$i/out.json 2> /tmp/rp_$i/err.txt
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_$i -o s -- python3 $R/bench.py --full --steps 20 --warmup 3 --cpu-sample 0 > /tmp/rp_$i/out.json 2> /tmp/rp_$i/err.txt
   python3 - $i $R <<'PY'
 import json, shutil, sys
 i, R = sys.argv[1], sys.argv[2]

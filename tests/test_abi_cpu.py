@@ -169,6 +169,47 @@ def test_bench_line_of_the_full_size_record_fits_the_drivers_tail():
     assert d["value"] == full["value"] and d["roofline"]["frac"] == full["roofline"]["frac"] and "workload" in d["config"]
 
 
+def test_bench_line_of_a_plain_run_has_the_contract_fields_alone():
+    """bench.compact_line on the record of a run without --full (the full-size record above with every block that only
+    --full computes taken out): the contract fields and the config, and nothing that the sections after the headline fill."""
+    import importlib.util
+    import json
+
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    with open(os.path.join(REPO, "profiles", "r06_bench_default_detail.json")) as fh:
+        full = json.load(fh)
+    plain = {k: v for k, v in full.items() if k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                                                    "scaling", "vs_baseline", "dtype", "data", "config", "value_first_allocation",
+                                                    "first_allocation")}
+    plain["per_rank"] = [{k: v for k, v in r.items() if k in ("rank", "device", "orfs", "nt", "step_device_ms", "algorithmic_bytes_per_launch")}
+                         for r in full["per_rank"]]
+    d = json.loads(json.dumps(bench.compact_line(plain)))
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"):
+        assert d[key] == full[key], key
+    assert d["config"]["workspace_placement"]["searched"] is True and d["value_first_allocation"] == full["value_first_allocation"]
+    assert d["per_rank"] == [{"rank": 0, "device": 0, "orfs": full["per_rank"][0]["orfs"], "nt": full["per_rank"][0]["nt"],
+                              "step_device_ms": full["per_rank"][0]["step_device_ms"]}]
+    for key in ("roofline", "cpu_baseline", "verify", "quality", "kernel_ms", "finish_ms", "step_frac", "fused", "fused_nested", "slice_projection",
+                "pipelined", "value_pipelined", "source_placed", "value_source_placed", "value_single_sample"):
+        assert key not in d, key
+
+
+def test_bench_full_is_an_option_off_by_default(monkeypatch):
+    import importlib.util
+    import sys
+
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    plain = ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"]
+    monkeypatch.setattr(sys, "argv", plain)
+    assert bench.parse_args().full is False
+    monkeypatch.setattr(sys, "argv", plain + ["--full"])
+    assert bench.parse_args().full is True
+
+
 def test_bench_dump_outputs_samples_a_large_set_the_same_way_every_time(tmp_path, monkeypatch):
     """bench.dump_outputs on host tensors: more ORFs than DUMP_MAX_ORFS -> the same sorted, seeded sample of rows in
     every call, each column as float64 at those rows; at most DUMP_MAX_ORFS rows of every array."""

@@ -21,7 +21,7 @@ def test_bench_line_has_the_contract_fields(tmp_path):
     detail_path = str(tmp_path / "detail.json")
     out = subprocess.run(
         [sys.executable, os.path.join(REPO, "bench.py"), "--orfs", "60000", "--steps", "3", "--warmup", "1", "--cpu-sample", "100",
-         "--cpu-cores", "4", "--detail", detail_path],
+         "--cpu-cores", "4", "--detail", detail_path, "--full"],
         capture_output=True, text=True, timeout=600, cwd=REPO,
     )
     assert out.returncode == 0, out.stderr[-2000:]
@@ -92,7 +92,7 @@ def test_two_ranks_shard_one_set_and_concat_equals_whole():
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--orfs", "300000", "--steps", "3",
-         "--warmup", "1"],
+         "--warmup", "1", "--full"],
         capture_output=True, text=True, timeout=900, cwd=REPO, env=env,
     )
     assert out.returncode == 0, out.stderr[-3000:]
@@ -129,7 +129,7 @@ def test_a_failing_rccl_probe_falls_back_to_gloo():
 
     if torch.cuda.device_count() >= 2:
         pytest.skip("needs ranks sharing a GPU to make RCCL fail")
-    d = _bare_bench(2, 200000, env_extra={"RP_BENCH_BACKEND": "nccl"})
+    d = _bare_bench(2, 200000, extra=("--full",), env_extra={"RP_BENCH_BACKEND": "nccl"})
     assert d["n_gpus"] == 2 and d["verify"]["ok"] is True and d["verify"]["orfs_checked"] == 200000
     assert d["config"]["control_backend"].startswith("gloo (RCCL probe failed")
 
@@ -145,7 +145,7 @@ def test_bare_command_runs_n_ranks(n):
     if n > phys and n > MAX_RANKS_SHARING_GPUS:
         pytest.skip(f"needs {n} GPUs, found {phys}: {n} ranks sharing them would keep a GPU open from more than "
                     f"{MAX_RANKS_SHARING_GPUS} processes at once")
-    d = _bare_bench(n, 400000)
+    d = _bare_bench(n, 400000, extra=("--full",))
     assert d["n_gpus"] == n and d["scaling"] == "strong" and d["config"]["launcher"] == "bench.py self_launch"
     assert d["config"]["physical_gpus"] == phys and d["config"]["ranks_share_gpus"] == (n > phys)
     assert d["config"]["control_backend"] == ("nccl" if phys >= n else "gloo")  # (RCCL is probed first; "gloo (RCCL probe failed ...)" would say so)
@@ -168,8 +168,8 @@ def test_one_rank_has_the_same_value_definition_with_and_without_a_process_group
     """N = 1 plain, and N = 1 with the N-rank control flow forced on (RP_BENCH_FORCE_DIST=1: RCCL init, barrier and
     max-over-ranks on the one GPU -- the branch the 8-GPU run takes): `value` = ORFs of the whole job * steps /
     max-over-ranks wall time of the K steps in both."""
-    plain = _bare_bench(1, 300000, extra=("--cpu-sample", "0", "--no-fused"))
-    forced = _bare_bench(1, 300000, extra=("--cpu-sample", "0", "--no-fused"), env_extra={"RP_BENCH_FORCE_DIST": "1"})
+    plain = _bare_bench(1, 300000, extra=("--cpu-sample", "0", "--no-fused", "--full"))
+    forced = _bare_bench(1, 300000, extra=("--cpu-sample", "0", "--no-fused", "--full"), env_extra={"RP_BENCH_FORCE_DIST": "1"})
     for d in (plain, forced):
         assert d["n_gpus"] == 1 and d["config"]["orfs_total"] == 300000 and d["verify"]["ok"] is True
         assert d["value"] == pytest.approx(300000 * d["steps"] / (d["ms_per_step"] * d["steps"] * 1e-3), rel=1e-9)
@@ -186,7 +186,7 @@ def test_pipelined_and_first_allocation_values_are_reported_beside_value(tmp_pat
     beside score(k + 1)) and `value_one_stream_repeat` (the same protocol on one stream right after it): both timings
     reported, neither chosen; the pipelined results equal the headline's bit for bit."""
     detail = str(tmp_path / "detail.json")
-    d = _bare_bench(1, 600000, extra=("--cpu-sample", "0", "--no-fused", "--detail", detail))
+    d = _bare_bench(1, 600000, extra=("--cpu-sample", "0", "--no-fused", "--detail", detail, "--full"))
     assert d["value"] == pytest.approx(600000 * d["steps"] / (d["ms_per_step"] * d["steps"] * 1e-3), rel=1e-9)
     assert d["value_first_allocation"] > 0 and d["first_allocation_ms_per_step"] > 0
     assert d["config"]["workspace_placement"]["searched"] is True
@@ -211,21 +211,57 @@ def test_pipelined_and_first_allocation_values_are_reported_beside_value(tmp_pat
 
 def test_dump_outputs_writes_the_last_timed_step_the_same_in_every_run(tmp_path):
     """`--dump-outputs DIR`: the per-ORF arrays of the last timed step as float64 .npy files, at most 64 MB, and the same
-    arrays from two runs with the same arguments (seeded inputs); `steps` / `ms_per_step` are the timed steps'."""
+    arrays from two runs with the same arguments (seeded inputs) -- one with --full, whose oracle check covers what the
+    steps computed, and one plain run; `steps` / `ms_per_step` are the timed steps' in both."""
     import numpy as np
 
     n = 50000
     runs = []
-    for k in range(2):
+    for k, mode in enumerate((("--full",), ())):
         d = _bare_bench(1, n, extra=("--cpu-sample", "0", "--no-fused", "--no-slice-projection", "--no-pipelined",
-                                     "--dump-outputs", str(tmp_path / f"run{k}")))
-        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["verify"]["ok"] is True  # (the oracle check of what the steps computed)
+                                     "--dump-outputs", str(tmp_path / f"run{k}"), *mode))
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        if mode:
+            assert d["verify"]["ok"] is True  # (the oracle check of what the steps computed)
+        else:
+            assert "verify" not in d
         runs.append({f[:-4]: np.load(str(tmp_path / f"run{k}" / f)) for f in os.listdir(str(tmp_path / f"run{k}"))})
     a, b = runs
-    assert set(a) == {"orf_index", "phase", "valid", "read_count", "min_codon_cov", "flags", "status"}
+    assert set(a) == set(b) == {"orf_index", "phase", "valid", "read_count", "min_codon_cov", "flags", "status"}
     assert sum(v.nbytes for v in a.values()) <= 64 << 20
     for key in a:
         assert a[key].dtype == np.float64 and a[key].shape == (n,), key
         assert np.array_equal(a[key], b[key]), key
     assert np.array_equal(a["orf_index"], np.arange(n))
     assert (a["read_count"] >= 0).all() and np.isin(a["status"], (0, 1)).all() and a["status"].any()
+
+
+# what only a --full run adds to the line
+FULL_ONLY = ("roofline", "cpu_baseline", "cpu_baseline_1core", "verify", "quality", "kernel_ms", "finish_ms", "step_frac", "fused", "fused_nested",
+             "slice_projection", "pipelined", "value_pipelined", "source_placed", "value_source_placed", "value_single_sample")
+
+
+def test_plain_run_times_the_headline_and_nothing_else(tmp_path):
+    """Without --full: set-up (with the workspace search and the steps before it, as in a --full run), warm-up, the timed
+    steps and the line -- the contract fields and the config, none of the sections that run after the headline."""
+    detail = str(tmp_path / "detail.json")
+    d = _bare_bench(1, 600000, extra=("--detail", detail))
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "dtype", "data", "config"):
+        assert key in d, key
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["unit"] == "ORFs/s"
+    assert d["value"] == pytest.approx(600000 * d["steps"] / (d["ms_per_step"] * d["steps"] * 1e-3), rel=1e-9)
+    assert d["config"]["orfs_total"] == 600000 and d["config"]["workspace_placement"]["searched"] is True
+    assert d["value_first_allocation"] > 0  # (the steps before the search run in both modes)
+    for key in FULL_ONLY:
+        assert key not in d, key
+    assert d["per_rank"][0]["step_device_ms"] > 0 and "kernel_ms" not in d["per_rank"][0]
+    record = json.load(open(detail))
+    assert record["value"] == d["value"] and record["config"]["workspace_placement"]["copies"] == 2  # (the same block as with --full)
+    for key in FULL_ONLY:
+        assert key not in record, key
+    # N ranks without a launcher: the same headline protocol, no concat == whole check
+    d2 = _bare_bench(2, 400000)
+    assert d2["n_gpus"] == 2 and [r["rank"] for r in d2["per_rank"]] == [0, 1] and sum(r["orfs"] for r in d2["per_rank"]) == 400000
+    assert d2["value"] == pytest.approx(400000 * d2["steps"] / (d2["ms_per_step"] * d2["steps"] * 1e-3), rel=1e-9)
+    for key in FULL_ONLY:
+        assert key not in d2, key
